@@ -8,12 +8,19 @@ relation (W=4096 x D=256), 1024 witnesses per GPU, synthetic inputs.  One
 checks, the verdict reduction) and, for N > 1, the RCCL all-reduce of the
 {satisfied, failed} counts.  Inputs are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-The default invocation (one GPU, C2) also measures the other three workloads -- BASELINE configs[3] (C4, GF(2)),
-configs[4] (C5, R1CS rows) and the structured For / Call / Switch relation -- and prints them under `secondary`, each
-with its own `roofline` and `cpu_baseline` (bounded samples; `--no-secondary` skips them).
+A plain invocation does what the headline figure needs and nothing else: it sets up the workload (the probe pass that
+makes the expected outputs included), warms up, times K steps and prints the line.  `--dump-outputs DIR` writes what
+the last timed step computed (rank 0's lanes) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared
+output for output.
+
+`--full` adds everything else: the CPU baselines, the relation-in -> first-verdict sessions, the PCIe-inclusive passes,
+the 4096-witness (C2) and 8192-witness (C4) variants, the check of the probe outputs against the committed golden
+hashes, and for one GPU and the default C2 the other workloads -- BASELINE configs[3] (C4, GF(2)), configs[4] (C5, R1CS
+rows), the structured For / Call / Switch relation and SHA-256 -- printed under `secondary`, each with its own
+`roofline` and `cpu_baseline` (bounded samples; `--no-secondary` skips them).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (child processes, started
 before anything in this process touches the GPU); rank 0 prints the JSON line.  With fewer than N devices visible
@@ -97,6 +104,25 @@ def check_probe_outputs(name, wl, outs, lane_offset):
     return covered
 
 
+def step_outputs(first_fail, counts, flags=None):
+    """What a caller of the timed path receives after a step, as float64 arrays: per lane the index of the first failing
+    check (AssertZero of the tape, row of the R1CS; -1 where every check held) and the lane flags of a replay, and the
+    {satisfied, failed} counts."""
+    ff = np.asarray(first_fail, dtype=np.uint32)
+    out = {'first_fail': np.where(ff == 0xFFFFFFFF, -1.0, ff.astype(np.float64)),
+           'counts': np.asarray(counts, dtype=np.float64)}
+    if flags is not None:
+        out['lane_flags'] = np.asarray(flags, dtype=np.float64)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: DIR/<name>.npy for every array (a few KB: one value per lane)"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 class _DevU64x2:
     """torch view of the engine's device counters {satisfied, failed}"""
 
@@ -139,8 +165,9 @@ def first_verdict_seconds(zk, wl, msgs, inst, wit, batch, stream, pinned, bool_p
             'worker_busy_s': round(info['worker_busy_s'], 4), 'satisfied': counts[0]}
 
 
-def build_session(zk, name, wl, batch, lane_offset, lane_group, bool_path=None, streams=2):
-    """probe pass for the expected outputs, then the real session with resident inputs"""
+def build_session(zk, name, wl, batch, lane_offset, lane_group, bool_path=None, streams=2, check_golden=True):
+    """probe pass for the expected outputs (checked against the golden hashes with check_golden), then the real session
+    with resident inputs"""
     t0 = time.time()
     if getattr(wl, 'closed_form', False):   # StructuredArith, Sha256Compress: the expected values come with the inputs, no probe pass
         inst, wit, n_bad = wl.inputs(batch, lane_offset)
@@ -169,7 +196,7 @@ def build_session(zk, name, wl, batch, lane_offset, lane_group, bool_path=None, 
     if wl.p == 2:
         outs = outs[:, :, 0]
     probe.close()
-    pinned_lanes = check_probe_outputs(name, wl, outs, lane_offset)
+    pinned_lanes = check_probe_outputs(name, wl, outs, lane_offset) if check_golden else 0
     n_bad = wl.set_expected_outputs(inst, outs, lane_offset)
     return finish_session(zk, wl, batch, lane_group, bool_path, streams, inst, wit, n_bad, t0, time.time(), pinned_lanes)
 
@@ -411,9 +438,10 @@ def compact_line(full, detail_path):
     return _r(line)
 
 
-def bench_c5(args, zk, workloads, ctx, steps, warmup, cpu_budget_s=15.0, coef_kind='random'):
+def bench_c5(args, zk, workloads, ctx, steps, warmup, cpu_budget_s=15.0, coef_kind='random', outputs=None):
     """BASELINE configs[4]: 2^20-row R1CS over BN254 (3+3+1 terms per row), witness batch 1024 per GPU.
     step = the row check <a,w>*<b,w> = <c,w> of every row for every lane + the count reduction.
+    `outputs` (a dict): filled with what the last timed step returned (step_outputs).
     coef_kind 'small': the same rows with coefficients 1 / -1 / 16-bit signed integers (workloads.R1csSynthetic), which the
     row kernel takes by its unit / small coefficient classes -- a variant next to the BASELINE line, never instead of it."""
     world, rank, dist, torch, red_dev, dist_on = ctx['world'], ctx['rank'], ctx['dist'], ctx['torch'], ctx['red_dev'], ctx['dist_on']
@@ -479,6 +507,8 @@ def bench_c5(args, zk, workloads, ctx, steps, warmup, cpu_budget_s=15.0, coef_ki
         dist.all_reduce(tm, op=dist.ReduceOp.MAX)
         elapsed = float(tm.item())
     assert total[0] == workloads.expected_satisfied(batch * world) and total[1] == batch * world - total[0], total
+    if outputs is not None:
+        outputs.update(step_outputs(ff, total))
     out = None
     if rank == 0:
         kernel_ms = float(np.mean(ms))
@@ -545,9 +575,10 @@ def bench_c5(args, zk, workloads, ctx, steps, warmup, cpu_budget_s=15.0, coef_ki
     return out
 
 
-def bench_tape(name, args, zk, workloads, ctx, steps, warmup, headline, cpu_budget_s=15.0):
+def bench_tape(name, args, zk, workloads, ctx, steps, warmup, headline, cpu_budget_s=15.0, outputs=None):
     """C2 (headline), C4 and the structured relation: one step = one replay of the recorded tape over the batch.
-    `headline`: the workload the command line names (its size flags apply; the extras of the headline line are measured)."""
+    `headline`: the workload the command line names (its size flags apply; the extras of the headline line are measured).
+    `outputs` (a dict): filled with what the last timed step left for the caller (step_outputs)."""
     world, rank, dist, torch, red_dev, dist_on = ctx['world'], ctx['rank'], ctx['dist'], ctx['torch'], ctx['red_dev'], ctx['dist_on']
     named = name == args.workload      # --width / --depth / --batch-per-gpu describe the workload named on the command line
     width, depth, bpg = (args.width, args.depth, args.batch_per_gpu) if named else (0, 0, 0)
@@ -576,7 +607,8 @@ def bench_tape(name, args, zk, workloads, ctx, steps, warmup, headline, cpu_budg
     # run at most 6 processes on its card, so the 8 lane shares of BASELINE configs[2] are rehearsed as two launches of 4
     rank_base = int(os.environ.get('ZKI_RANK_BASE', '0'))
     lane_offset = (rank_base + rank) * batch
-    ev, inst, wit, n_bad, msgs, host = build_session(zk, name, wl, batch, lane_offset, lane_group, bool_path, args.streams)
+    ev, inst, wit, n_bad, msgs, host = build_session(zk, name, wl, batch, lane_offset, lane_group, bool_path, args.streams,
+                                                     check_golden=args.full)
     kinds, _, _ = ev.tape()
     # structured: the unit of work is one backend call of the reference's evaluator (every value-returning call it
     # makes for one witness, ladders and scope copies included) -- what the CPU baseline executes call by call
@@ -642,6 +674,9 @@ def bench_tape(name, args, zk, workloads, ctx, steps, warmup, headline, cpu_budg
         assert [r['rank'] for r in ranks_seen] == list(range(world)), ranks_seen
         for r in ranks_seen:
             assert r['satisfied'] == workloads.expected_satisfied(r['lanes'], r['lane_offset']), r
+    if outputs is not None:
+        ff, flags = ev.lane_results(batch)
+        outputs.update(step_outputs(ff, total, flags))
     # PCIe-inclusive figure (never `value`): the boundary hands over host buffers every step
     pcie_ms = None
     if world == 1 and headline and not structured and not args.timed_steps_only:
@@ -877,9 +912,17 @@ def main():
     ap.add_argument('--full-line', action='store_true', help='print everything on the line (default: the compact line; the rest in the detail file)')
     ap.add_argument('--timed-steps-only', action='store_true',
                     help='nothing but the probe, the warm-up and the timed steps (what a rocprofv3 trace of the timed region needs): '
-                         '= --no-cpu-baseline --no-hbm-variant --no-first-verdict --no-secondary and no PCIe-inclusive passes')
+                         '= --no-cpu-baseline --no-hbm-variant --no-first-verdict --no-secondary and no PCIe-inclusive passes '
+                         '(what a run without --full does anyway)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: CPU baselines, first-verdict sessions, '
+                         'PCIe-inclusive passes, the 4096 / 8192-witness variants, the probe outputs against the golden hashes, '
+                         'the secondary workloads (the --no-* switches above then leave parts out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (rank 0\'s lanes) as DIR/<name>.npy, float64')
     args = ap.parse_args()
-    if args.timed_steps_only:
+    if args.timed_steps_only or not args.full:
+        args.timed_steps_only = True
         args.no_cpu_baseline = args.no_hbm_variant = args.no_first_verdict = args.no_secondary = True
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -919,10 +962,13 @@ def main():
     ctx = {'world': world, 'rank': rank, 'dist': dist, 'torch': torch, 'red_dev': red_dev, 'dist_on': dist_on,
            'backend': backend, 'n_dev': n_dev, 'dev_index': dev_index}
 
+    outputs = {} if args.dump_outputs else None
     if args.workload == 'c5':
-        out = bench_c5(args, zk, workloads, ctx, args.steps, args.warmup, coef_kind=args.coefs)
+        out = bench_c5(args, zk, workloads, ctx, args.steps, args.warmup, coef_kind=args.coefs, outputs=outputs)
     else:
-        out = bench_tape(args.workload, args, zk, workloads, ctx, args.steps, args.warmup, True)
+        out = bench_tape(args.workload, args, zk, workloads, ctx, args.steps, args.warmup, True, outputs=outputs)
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     default_c2 = args.workload == 'c2' and not (args.width or args.depth or args.batch_per_gpu or args.lane_group)
     if rank == 0 and world == 1 and not dist_on and default_c2 and not args.no_secondary:
         # the other workloads, measured in this same invocation with bounded CPU samples (a few seconds each)

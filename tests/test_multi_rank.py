@@ -85,13 +85,13 @@ def test_configs2_lane_shares_at_full_size_in_two_launches_of_four_ranks():
     """BASELINE configs[2]: the full 2^20-gate BN254 relation, 8 ranks x 1024 witnesses.  The pool allows at most 6
     processes on one card, so the 8 lane shares are rehearsed as two launches of 4 ranks (ZKI_RANK_BASE = 0 and 4), each
     rank with its own engine, 263 MB wire table and 1024-lane share at its global lane offset; every rank's probe outputs
-    are checked against tests/golden/c2_all_lanes.json (all 8192 lanes) inside bench.py, the counts are reduced over the
+    are checked against tests/golden/c2_all_lanes.json (all 8192 lanes) inside bench.py --full, the counts are reduced over the
     process group, and `ranks_seen` comes from an all_gather over it.  Together: 8192 - 85 satisfied."""
     sat = 0
     for base in (0, 4):
         os.environ['ZKI_RANK_BASE'] = str(base)
         try:
-            r = run_bench('--gpus', 4, '--steps', 2, '--warmup', 1, '--no-cpu-baseline', timeout=900)
+            r = run_bench('--gpus', 4, '--steps', 2, '--warmup', 1, '--full', '--no-cpu-baseline', timeout=900)
         finally:
             del os.environ['ZKI_RANK_BASE']
         assert r['n_gpus'] == 4 and r['config']['rank_base'] == base and r['config']['batch_per_gpu'] == 1024

@@ -27,10 +27,10 @@ pmc() {  # pmc <name> <counters...> -- <bench args...>
   cp $(find /tmp/pmc_$name -name '*counter_collection.csv' | head -1) /tmp/pmc_$name.csv
 }
 if [ $WHAT = bench ]; then
-  # the driver's command: the C2 headline line with the c4 / c5 / structured lines under `secondary`
-  echo "[collect] bench (default invocation)"
+  # --full: the C2 headline line with roofline_hbm, cpu_baseline, first verdict and the other workloads under `secondary`
+  echo "[collect] bench (--full invocation)"
   # (the line is the compact one the driver records; everything else is in the detail file the run writes)
-  ZKI_BENCH_DETAIL=gpurun_out/$TAG/${TAG}_bench_detail.json timeout -k 10 900 $B --steps 20 --warmup 3 > $OUT/${TAG}_bench_default.json 2> $OUT/bench_default.err
+  ZKI_BENCH_DETAIL=${OUT#$ROOT/}/${TAG}_bench_detail.json timeout -k 10 900 $B --full --steps 20 --warmup 3 > $OUT/${TAG}_bench_default.json 2> $OUT/bench_default.err
   python3 - $OUT $TAG <<'PY'
 import json, sys
 out, tag = sys.argv[1], sys.argv[2]
@@ -94,7 +94,7 @@ elif [ $WHAT = pmc_c45 ]; then
   python3 $ROOT/tools/pmc_summary.py /tmp/pmc_c4_lds_unbanked.csv bool_lds_kernel 1000 > $OUT/${TAG}_pmc_c4_lds_counters_bank_unaware.json
   # the same relation shape with gate j reading wires j and j+1 of the previous layer: conflict-free by construction,
   # same program size -- what is left is the program stream and the barriers
-  ZKI_C4_WIRING=identity ZKI_BENCH_DETAIL=gpurun_out/$TAG/${TAG}_bench_c4_identity_detail.json $B --workload c4 --steps 10 --warmup 2 --no-cpu-baseline --no-first-verdict > $OUT/${TAG}_bench_c4_identity_wiring.json 2> $OUT/bench_c4_identity.err
+  ZKI_C4_WIRING=identity ZKI_BENCH_DETAIL=${OUT#$ROOT/}/${TAG}_bench_c4_identity_detail.json $B --workload c4 --steps 10 --warmup 2 --full --no-cpu-baseline --no-first-verdict > $OUT/${TAG}_bench_c4_identity_wiring.json 2> $OUT/bench_c4_identity.err
   C5="--workload c5 --steps 2 --warmup 1 --timed-steps-only"
   K5='r1cs_row_kernel<8, false, false>'
   pmc c5_f FETCH_SIZE -- $C5
