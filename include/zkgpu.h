@@ -312,6 +312,12 @@ int zkgpu_field_representation(const zkgpu_session* s, uint32_t k);
  * Returns 0, 1 for an unknown op, 2 for a modulus the path does not take (0, 1, more than 4096 bits). */
 int zkgpu_generic_selftest(const uint8_t* modulus_le, size_t modulus_len, int op, const uint32_t* a, const uint32_t* b,
                            uint32_t* out, uint32_t* nwords);
+/* Test hook: the arithmetic of the R1CS kernels of the any-modulus path run on the host.  op 0: out = sum over k < n_terms
+ * of y[k] * x[k] mod p (x, y: n_terms values each, y the coefficients), 1: the same with every coefficient 1 (y unused),
+ * 2: out = (x + y - z) / p, 3: out = (x * y - z) / p (one value each; y may be >= p, z must be (x op y) mod p).  Values
+ * hold *nwords 32-bit words; returns as zkgpu_generic_selftest does. */
+int zkgpu_r1cs_generic_selftest(const uint8_t* modulus_le, size_t modulus_len, int op, uint32_t n_terms, const uint32_t* x,
+                                const uint32_t* y, const uint32_t* z, uint32_t* out, uint32_t* nwords);
 uint64_t zkgpu_rccl_reductions(const zkgpu_session* s);       /* zkgpu_counts calls answered by an RCCL all-reduce */
 size_t zkgpu_rccl_note(const zkgpu_session* s, char* buf, size_t cap); /* why RCCL was not used ("" = it was, or was not needed) */
 int zkgpu_lane_results(zkgpu_session* s, uint32_t* first_fail, uint32_t* flags); /* [batch] each */
@@ -331,7 +337,10 @@ uint64_t zkgpu_table_bytes(const zkgpu_session* s);
  * is the constant one, :117; variables are numbered in allocation order); the assignment of a batch is
  * what the replay leaves in the wire table (zkgpu_finalize(retain_all=1)); zkgpu_r1cs_check evaluates
  * <a,w>*<b,w> = <c,w> for every row and lane on the GPU (the job of the zkinterface Simulator the
- * reference's tests call, :583-589). */
+ * reference's tests call, :583-589).  Every arithmetic field the session works in is taken, like the converter's
+ * BigUint arithmetic: odd characteristics of at most 512 bits run the Montgomery row kernels, the rest (even ones, the
+ * rings Z/2^k, up to 4096 bits) the any-modulus ones (canonical residues, zkgpu_field_representation 2).  Not available:
+ * GF(2) (bit-packed wires) and a session whose field changes between Relation messages. */
 int zkgpu_r1cs_from_tape(zkgpu_session* s, int use_correction);
 /* out[0]=rows out[1]=variables out[2]=terms out[3]=distinct coefficients */
 int zkgpu_r1cs_info(const zkgpu_session* s, uint64_t out[4]);
@@ -339,7 +348,8 @@ int zkgpu_r1cs_info(const zkgpu_session* s, uint64_t out[4]);
  * products with the pool), out[1] every coefficient 1 or -1 (additions), out[2] every coefficient a signed integer
  * below 2^31 in magnitude (N word products per term instead of N^2; what FromR1CSConverter expansions mostly hold,
  * from_r1cs.rs:110-125).  Option "r1cs_coef_classes" = "0" (before the rows are made) sends every combination down
- * the first path. */
+ * the first path.  A field of the any-modulus path has the first path alone: every combination counts there, whatever
+ * the option says (it is accepted and has no effect). */
 int zkgpu_r1cs_class_counts(const zkgpu_session* s, uint64_t out[3]);
 /* row_ptr: 3 entries per row (start of A, B, C in the term arrays) + final end; var_of_op[i] = variable of
  * tape op i (0xFFFF...F for assert_zero).  Any pointer may be NULL. */
@@ -369,7 +379,8 @@ int zkgpu_r1cs_get_vars(zkgpu_session* s, const uint64_t* vars, uint32_t n_vars,
 /* The quotient ("correction") wires of ToR1CSConverter with use_correction (to_r1cs.rs:163-211,213-260,262-359): for
  * the listed recorded calls (tape indices of add / multiply / add_constant / mul_constant / not calls; the correction
  * variable of call i is var_of_op[i] + 1 of zkgpu_r1cs_export) the integer q = (a op b) / p of every lane, computed on
- * the GPU from the retain_all wire table of the last replay: out[lane][k][elem_bytes], little-endian. */
+ * the GPU from the retain_all wire table of the last replay: out[lane][k][elem_bytes], little-endian.  Any modulus: for
+ * p = 2^s * m (m odd) the exact division is a shift by s and a product with m^-1 mod 2^(8 elem_bytes). */
 int zkgpu_r1cs_correction_values(zkgpu_session* s, const uint64_t* tape_ops, uint32_t n_ops, uint8_t* out);
 float zkgpu_r1cs_last_ms(const zkgpu_session* s);             /* HIP-event time of the last check */
 

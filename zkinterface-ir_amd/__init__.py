@@ -113,6 +113,7 @@ def lib():
         'zkgpu_field_segment_carried': (ci, [vp, u32, u32p, u32]),
         'zkgpu_field_representation': (ci, [vp, u32]),
         'zkgpu_generic_selftest': (ci, [ctypes.c_char_p, sz, ci, vp, vp, vp, u32p]),
+        'zkgpu_r1cs_generic_selftest': (ci, [ctypes.c_char_p, sz, ci, ctypes.c_uint32, vp, vp, vp, vp, u32p]),
         'zkgpu_rccl_reductions': (u64, [vp]),
         'zkgpu_rccl_note': (sz, [vp, ctypes.c_char_p, sz]),
         'zkgpu_lane_results': (ci, [vp, vp, vp]),
@@ -664,6 +665,33 @@ def generic_selftest(p, op, a, b=0):
     rc = L.zkgpu_generic_selftest(mod, len(mod), {'add': 0, 'mul': 1, 'reduce': 2, 'and': 3, 'xor': 4}[op], A, B, out, ctypes.byref(nw))
     if rc:
         raise ZkGpuError('zkgpu_generic_selftest failed (%d)' % rc)
+    return sum(int(out[i]) << (32 * i) for i in range(n))
+
+
+def r1cs_generic_selftest(p, op, x, y=None, z=0):
+    """Test hook (include/zkgpu.h zkgpu_r1cs_generic_selftest): the arithmetic of the any-modulus R1CS kernels on the host,
+    Python integers in and out.  op 'lincomb': sum of y[k] * x[k] mod p (y None: coefficients 1); 'add_quotient' /
+    'mul_quotient': (x + y - z) / p, (x * y - z) / p for single values x, y, z."""
+    L = lib()
+    mod = int(p).to_bytes((int(p).bit_length() + 7) // 8 or 1, 'little')
+    nw = ctypes.c_uint32(0)
+    rc = L.zkgpu_r1cs_generic_selftest(mod, len(mod), 0, 0, None, None, None, None, ctypes.byref(nw))
+    if rc:
+        raise ZkGpuError('zkgpu_r1cs_generic_selftest: the modulus is not supported (%d)' % rc)
+    n = nw.value
+
+    def words(vals):
+        return (ctypes.c_uint32 * max(1, n * len(vals)))(*[(int(v) >> (32 * i)) & 0xFFFFFFFF for v in vals for i in range(n)])
+    if op == 'lincomb':
+        code, n_terms = (0 if y is not None else 1), len(x)
+        X, Y, Z = words(x), words(y if y is not None else []), words([])
+    else:
+        code, n_terms = {'add_quotient': 2, 'mul_quotient': 3}[op], 1
+        X, Y, Z = words([x]), words([y]), words([z])
+    out = (ctypes.c_uint32 * n)()
+    rc = L.zkgpu_r1cs_generic_selftest(mod, len(mod), code, n_terms, X, Y, Z, out, ctypes.byref(nw))
+    if rc:
+        raise ZkGpuError('zkgpu_r1cs_generic_selftest failed (%d)' % rc)
     return sum(int(out[i]) << (32 * i) for i in range(n))
 
 

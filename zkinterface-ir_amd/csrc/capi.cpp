@@ -1001,8 +1001,9 @@ void build_device_rows(zkgpu_session* s, SlotOf&& slot_of_var) {
         b_is_one = last.slot == 0xFFFFFFFFu && last.coef == 0xFFFFFFFFu;
       }
       // the coefficient class of the combination (device/args.hpp).  All coefficients 1: class full, whose terms of
-      // coefficient 1 are plain additions already (and what zkgpu_r1cs_assign expects of C).
-      if (s->r1cs_coef_classes && n[part] && all_small && !(all_unit && !any_minus) && !(part == 1 && b_is_one)) {
+      // coefficient 1 are plain additions already (and what zkgpu_r1cs_assign expects of C).  A field of the any-modulus
+      // path has class full alone (the other classes are a form of the Montgomery row kernel).
+      if (s->r1cs_coef_classes && !s->backend.field().generic && n[part] && all_small && !(all_unit && !any_minus) && !(part == 1 && b_is_one)) {
         cls[part] = all_unit ? kR1csClassUnit : kR1csClassSmall;
         size_t k = first_term;
         for (uint32_t t = t0; t < t1; ++t) {
@@ -1280,6 +1281,19 @@ int zkgpu_generic_selftest(const uint8_t* modulus_le, size_t modulus_len, int op
     if (nwords) *nwords = f.nwords;
     if (!a) return 0;   // (a query for the width)
     return Engine::generic_selftest(f, op, a, b, out);
+  } catch (const std::exception&) {
+    return 2;
+  }
+}
+// ... and that of the R1CS kernels of the any-modulus path (zkgpu.h)
+int zkgpu_r1cs_generic_selftest(const uint8_t* modulus_le, size_t modulus_len, int op, uint32_t n_terms, const uint32_t* x,
+                                const uint32_t* y, const uint32_t* z, uint32_t* out, uint32_t* nwords) {
+  try {
+    FieldHost f;
+    f.init(Value(modulus_le, modulus_le + modulus_len), true);
+    if (nwords) *nwords = f.nwords;
+    if (!x) return 0;   // (a query for the width)
+    return Engine::r1cs_generic_selftest(f, op, n_terms, x, y, z, out);
   } catch (const std::exception&) {
     return 2;
   }
@@ -1973,8 +1987,8 @@ int zkgpu_r1cs_from_tape(zkgpu_session* s, int use_correction) {
   return guarded(s, [&] {
     single_segment_only(s, "the R1CS conversion");
     if (!s->backend.field_set()) throw std::runtime_error("no Relation ingested: the field is not set");
-    if (s->backend.field().is_two || s->backend.field().generic)
-      throw std::runtime_error("R1CS conversion on the GPU path needs an odd field characteristic of at most 512 bits");
+    if (s->backend.field().p_is_two())
+      throw std::runtime_error("R1CS conversion on the GPU path is not available over GF(2) (bit-packed wires)");
     const Tape& t = s->backend.tape();
     Value modulus(4 * kFieldWords, 0);
     for (int i = 0; i < 4 * kFieldWords; ++i) modulus[i] = (uint8_t)(s->backend.field().p[i / 4] >> (8 * (i % 4)));
@@ -2038,8 +2052,7 @@ int zkgpu_r1cs_load_csr(zkgpu_session* s, uint32_t n_rows, const uint32_t* row_p
   return guarded(s, [&] {
     single_segment_only(s, "zkgpu_r1cs_load_csr");
     if (!s->finalized || !s->retain_all) throw std::runtime_error("zkgpu_finalize(retain_all=1) first: variables are tape values");
-    if (s->backend.field().is_two || s->backend.field().generic)
-      throw std::runtime_error("R1CS rows on the GPU path need an odd field characteristic of at most 512 bits");
+    if (s->backend.field().p_is_two()) throw std::runtime_error("R1CS rows on the GPU path are not available over GF(2) (bit-packed wires)");
     if (s->engine_loaded) throw std::runtime_error("load the CSR before the first zkgpu_set_inputs* call (the table is sized once)");
     if (!row_ptr || (n_coefs && (!coef_bytes || coef_width == 0)))
       throw std::runtime_error("zkgpu_r1cs_load_csr: row_ptr / coefficient bytes missing or coef_width is 0");
@@ -2150,7 +2163,7 @@ int zkgpu_r1cs_correction_values(zkgpu_session* s, const uint64_t* tape_ops, uin
     if (!s->retain_all) throw std::runtime_error("zkgpu_finalize(retain_all=1) is required: the quotients are computed from the wire values");
     const Tape& t = s->backend.tape();
     const FieldHost& f = s->backend.field();
-    if (f.is_two || f.generic) throw std::runtime_error("quotient wires need an odd field characteristic of at most 512 bits");
+    if (f.p_is_two()) throw std::runtime_error("quotient wires are not available over GF(2) (bit-packed wires)");
     const uint32_t one_const = (uint32_t)t.consts.size();   // the literal 1 of `not` = add_constant(a, 1) (to_r1cs.rs:369-371)
     std::vector<uint32_t> calls, const_words((size_t)(t.consts.size() + 1) * f.nwords, 0);
     for (size_t c = 0; c < t.consts.size(); ++c) {

@@ -259,6 +259,24 @@ void launch_dump_generic(dim3 grid, hipStream_t st, const uint4* table, u32 n_sl
 // hold gp->nwords words (op 2: a holds gp->nwords raw words).  Returns 0, or 1 for an unknown op.
 int generic_selftest(const GenericParams* gp, int op, const u32* a, const u32* b, u32* out);
 
+// R1CS over that path (kernels_r1cs_generic.hip, device/r1cs_generic_kernels.hpp).  The exact division of the quotient
+// kernel: p = 2^shift * m with m odd; lives in device memory (512 B of inverse at 4096 bits).
+struct GenericCorrParams {
+  u32 shift;
+  u32 minv[kGenericMaxWords];   // m^{-1} mod 2^(32 nwords)
+};
+// R1csArgs::coefs holds canonical words (nwords each), canonical 1 at one_coef; every combination is of class full
+void launch_r1cs_generic(bool assign, dim3 grid, hipStream_t st, const R1csArgs& a, const GenericParams* gp_device, u32 nwords,
+                         u32 k_words);
+// R1csCorrArgs::pinv is not read: the division takes cp_device (generic_quotient_params)
+void launch_r1cs_corr_generic(dim3 grid, hipStream_t st, const R1csCorrArgs& a, const GenericParams* gp_device,
+                              const GenericCorrParams* cp_device, u32 nwords);
+void generic_quotient_params(const GenericParams* gp, GenericCorrParams* cp);   // host
+// the R1CS arithmetic run on the HOST (the same functions): op 0: out = sum of y_i * x_i over n terms, op 1: the same with
+// every coefficient 1 (y unused), op 2: out = (x + y - z) / p, op 3: out = (x * y - z) / p (x, y, z: one value each, y
+// may be >= p).  Every value holds gp->nwords words.  Returns 0, or 1 for an unknown op.
+int r1cs_generic_selftest(const GenericParams* gp, int op, u32 n, const u32* x, const u32* y, const u32* z, u32* out);
+
 void launch_verdict(dim3 grid, hipStream_t st, const u32* first_fail, const u32* lane_flags, u32 batch,
                     unsigned long long* counts);
 void launch_pack_inputs(hipStream_t st, const uint8_t* inst, u32 n_inst, const uint8_t* strict_inst, u64* packed_inst,

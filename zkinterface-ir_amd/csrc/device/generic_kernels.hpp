@@ -389,6 +389,7 @@ __global__ __launch_bounds__(256) void replay_generic_kernel(const ReplayArgs ar
   }
 }
 
+#ifndef ZKGPU_GENERIC_NO_DUMP   // (defined by a translation unit other than kernels_generic.hip that includes this header)
 // out[lane][k][n words]: canonical little-endian words of the listed slots (Evaluator::get, evaluator.rs:750-752)
 __global__ __launch_bounds__(64) void dump_generic_kernel(const uint4* __restrict__ table, u32 n_slots, const u32* __restrict__ slots,
                                                           u32 n_dump, u32 batch, u32* __restrict__ out, u32 n) {
@@ -410,6 +411,7 @@ __global__ __launch_bounds__(64) void dump_generic_kernel(const uint4* __restric
     }
   }
 }
+#endif  // ZKGPU_GENERIC_NO_DUMP
 #endif  // __HIPCC__
 
 }  // namespace zkgpu

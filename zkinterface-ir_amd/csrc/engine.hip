@@ -924,7 +924,15 @@ int Engine::generic_selftest(const FieldHost& f, int op, const uint32_t* a, cons
   return zkgpu::generic_selftest(&gp, op, a, b, out);
 }
 
-// (R1CS sessions are refused for fields of the any-modulus path in capi.cpp: the row kernels are Montgomery kernels)
+int Engine::r1cs_generic_selftest(const FieldHost& f, int op, uint32_t n, const uint32_t* x, const uint32_t* y, const uint32_t* z,
+                                  uint32_t* out) {
+  if (!f.generic) return 1;
+  const zkgpu::GenericParams gp = generic_params(f);
+  return zkgpu::r1cs_generic_selftest(&gp, op, n, x, y, z, out);
+}
+
+// A field of the any-modulus path (generic_) runs the row kernels of device/r1cs_generic_kernels.hpp: the pool holds
+// canonical words, every combination is of class full.
 void Engine::r1cs_upload(const std::vector<R1csRowDev>& rows, const std::vector<R1csTermDev>& terms,
                          const std::vector<uint32_t>& coef_words) {
   use_device();
@@ -947,6 +955,8 @@ void Engine::r1cs_upload(const std::vector<R1csRowDev>& rows, const std::vector<
         if (terms[t].slot != 0xFFFFFFFFu && terms[t].slot >= n_table_slots)
           throw std::runtime_error("Engine: R1CS term " + std::to_string(t) + " names a wire-table slot out of range");
         const uint32_t c = terms[t].coef;
+        if (generic_ && cls[part] != zkgpu::kR1csClassFull)
+          throw std::runtime_error("Engine: R1CS term " + std::to_string(t) + ": coefficient classes are a Montgomery-path form");
         if (cls[part] == zkgpu::kR1csClassFull) {
           if (c != 0xFFFFFFFFu && c >= n_coefs) throw std::runtime_error("Engine: R1CS term " + std::to_string(t) + " names a coefficient out of range");
         } else {
@@ -967,11 +977,16 @@ void Engine::r1cs_upload(const std::vector<R1csRowDev>& rows, const std::vector<
   zkgpu::FieldParams fpar;
   memcpy(&fpar, field_params_, sizeof fpar);
   std::vector<uint32_t> pool(coef_words);
-  pool.insert(pool.end(), fpar.one, fpar.one + nwords_);
   r1cs_one_coef_ = (uint32_t)n_coefs;
+  if (generic_) {   // canonical 1: the value of the constant one (the characteristic is at least 3)
+    pool.resize(pool.size() + nwords_, 0);
+    pool[(size_t)n_coefs * nwords_] = 1;
+  } else {
+    pool.insert(pool.end(), fpar.one, fpar.one + nwords_);
+  }
   // ... and behind it the Montgomery forms of 2^64 and 2^128 (R mod p doubled 64 and 128 times): what a product of
   // small-class sums is multiplied by when it is stored (r1cs_row_kernel, ASSIGN)
-  {
+  if (!generic_) {
     std::vector<uint32_t> x(fpar.one, fpar.one + nwords_);
     auto twice = [&]() {
       uint64_t c = 0;
@@ -1046,7 +1061,10 @@ void Engine::r1cs_run(bool assign, uint32_t first_row, uint32_t n_rows) {
   a.first_fail = (zkgpu::u32*)d_r1cs_fail_;
   a.one_coef = r1cs_one_coef_;
   const dim3 grid((n_rows + 3) / 4, lane_blocks_);
-  launch_r1cs(nwords_, assign, r1cs_classes_, grid, st, a, fp);
+  if (generic_)
+    zkgpu::launch_r1cs_generic(assign, grid, st, a, (const zkgpu::GenericParams*)d_generic_params_, nwords_, generic_k_words_);
+  else
+    launch_r1cs(nwords_, assign, r1cs_classes_, grid, st, a, fp);
   HIP_OK(hipGetLastError());
 }
 
@@ -1069,7 +1087,8 @@ void Engine::r1cs_corrections(const std::vector<uint32_t>& calls4, const std::ve
   zkgpu::R1csCorrArgs a;
   memset(&a, 0, sizeof a);
   // p^{-1} mod 2^(32 * nwords) by Hensel lifting from -n0inv = p^{-1} mod 2^32: x <- x * (2 - p * x)
-  {
+  // (the any-modulus path: generic_quotient_params below)
+  if (!generic_) {
     const uint32_t N = nwords_;
     std::vector<uint32_t> x(N, 0), t(N), u(N);
     x[0] = 0u - fp.n0inv;
@@ -1113,11 +1132,23 @@ void Engine::r1cs_corrections(const std::vector<uint32_t>& calls4, const std::ve
   a.consts = (const zkgpu::u32*)d_consts;
   a.out = (zkgpu::u32*)d_out;
   const dim3 grid((n + 3) / 4, lane_blocks_);
-  switch (nwords_) {
+  void* d_corr = nullptr;
+  if (generic_) {   // p = 2^s * m: s and m^{-1} mod 2^(32 nwords), computed here, read by the kernel from device memory
+    zkgpu::GenericParams gp;
+    HIP_OK(hipMemcpy(&gp, d_generic_params_, sizeof gp, hipMemcpyDeviceToHost));
+    zkgpu::GenericCorrParams cp;
+    zkgpu::generic_quotient_params(&gp, &cp);
+    HIP_OK(hipMalloc(&d_corr, sizeof cp));
+    HIP_OK(hipMemcpy(d_corr, &cp, sizeof cp, hipMemcpyHostToDevice));
+    zkgpu::launch_r1cs_corr_generic(grid, st, a, (const zkgpu::GenericParams*)d_generic_params_, (const zkgpu::GenericCorrParams*)d_corr,
+                                    nwords_);
+  } else {
+    switch (nwords_) {
 #define X(W) case W: zkgpu::launch_r1cs_corr_w##W(grid, st, a, fp); break;
-    ZK_WIDTHS(X)
+      ZK_WIDTHS(X)
 #undef X
-    default: throw std::runtime_error("Engine: unsupported limb count");
+      default: throw std::runtime_error("Engine: unsupported limb count");
+    }
   }
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(st));
@@ -1125,6 +1156,7 @@ void Engine::r1cs_corrections(const std::vector<uint32_t>& calls4, const std::ve
   (void)hipFree(d_calls);
   (void)hipFree(d_consts);
   (void)hipFree(d_out);
+  if (d_corr) (void)hipFree(d_corr);
 }
 
 void Engine::r1cs_finish_check() {

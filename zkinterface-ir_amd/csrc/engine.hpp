@@ -43,6 +43,10 @@ class Engine {
   // the CPU-tier tests: op 0 add, 1 mul, 2 reduce(a), 3 and, 4 xor over f.nwords words each.  Returns non-zero if `f`
   // is not a generic field or the op is unknown.
   static int generic_selftest(const FieldHost& f, int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
+  // ... and of the R1CS kernels of that path (device/r1cs_generic_kernels.hpp): op 0 a combination of n terms
+  // (x: values, y: coefficients), 1 the same with coefficients 1, 2 / 3 the quotient (x + y - z) / p, (x * y - z) / p
+  static int r1cs_generic_selftest(const FieldHost& f, int op, uint32_t n, const uint32_t* x, const uint32_t* y, const uint32_t* z,
+                                   uint32_t* out);
   // Bytes per input value the batch buffers must use: 4*nwords (arithmetic) or 1 (GF(2)).
   uint32_t elem_bytes() const { return elem_bytes_; }
 
@@ -80,7 +84,7 @@ class Engine {
   // or 2 (carried in from the previous field segment): what Evaluator::get returns for a wire that is a copy of an input
   void read_input(uint32_t stream, uint32_t position, std::vector<uint8_t>* out, uint32_t* width);
 
-  // ---- R1CS rows over the same wire table (arithmetic fields) ----------------------------------
+  // ---- R1CS rows over the same wire table (arithmetic fields: Montgomery kernels, or the any-modulus ones) -------
   // extra table slots behind the program's own (variables assigned by r1cs_run(assign=true)); call
   // before set_batch()
   void reserve_extra_slots(uint32_t n);

@@ -396,6 +396,8 @@ class R1csSynthetic:
         picks = np.where(picks >= n_base, picks + 1, picks)              # skip E's id
         self.coef_idx = rng.integers(0, n_coefs, size=(M, 6), dtype=np.int64)
         self.coefs = random_field_elements(seed + 17, (n_coefs,), p)[:, :self.width]
+        if self.width > self.coefs.shape[-1]:   # (as in witnesses(): below 2^256, zero-extended to the field's width)
+            self.coefs = np.concatenate([self.coefs, np.zeros((n_coefs, self.width - self.coefs.shape[-1]), dtype=np.uint8)], axis=-1)
         if coef_kind == 'small':
             crng = np.random.default_rng(seed + 18)
             u = crng.random(n_coefs)
