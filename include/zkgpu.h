@@ -318,6 +318,14 @@ int zkgpu_generic_selftest(const uint8_t* modulus_le, size_t modulus_len, int op
  * hold *nwords 32-bit words; returns as zkgpu_generic_selftest does. */
 int zkgpu_r1cs_generic_selftest(const uint8_t* modulus_le, size_t modulus_len, int op, uint32_t n_terms, const uint32_t* x,
                                 const uint32_t* y, const uint32_t* z, uint32_t* out, uint32_t* nwords);
+/* Test hook: the per-field constants the Montgomery kernels are launched with (an odd characteristic of at most 512
+ * bits), derived on the host exactly as a session's engine derives them; no device is touched.  p, r2 = R^2 mod p and
+ * one = R mod p (R = 2^(32 * nwords)) hold 16 words each, the words above nwords zero; out = {nwords, n0inv = -1/p mod 2^32,
+ * dot_rounds[0..3], lazy_dot3}: dot_rounds[K - 1] conditional subtractions make a lazily reduced sum of K Montgomery
+ * products canonical, lazy_dot3 != 0 lets a sum of three stay unreduced as an operand of a product of two such sums.
+ * Returns 0, or 2 for a modulus that path does not take (0, 1, 2, even, wider than 512 bits). */
+int zkgpu_mont_field_params(const uint8_t* modulus_le, size_t modulus_len, uint32_t* p, uint32_t* r2, uint32_t* one,
+                            uint32_t out[7]);
 uint64_t zkgpu_rccl_reductions(const zkgpu_session* s);       /* zkgpu_counts calls answered by an RCCL all-reduce */
 size_t zkgpu_rccl_note(const zkgpu_session* s, char* buf, size_t cap); /* why RCCL was not used ("" = it was, or was not needed) */
 int zkgpu_lane_results(zkgpu_session* s, uint32_t* first_fail, uint32_t* flags); /* [batch] each */

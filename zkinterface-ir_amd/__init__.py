@@ -113,6 +113,7 @@ def lib():
         'zkgpu_field_segment_carried': (ci, [vp, u32, u32p, u32]),
         'zkgpu_field_representation': (ci, [vp, u32]),
         'zkgpu_generic_selftest': (ci, [ctypes.c_char_p, sz, ci, vp, vp, vp, u32p]),
+        'zkgpu_mont_field_params': (ci, [ctypes.c_char_p, sz, vp, vp, vp, vp]),
         'zkgpu_r1cs_generic_selftest': (ci, [ctypes.c_char_p, sz, ci, ctypes.c_uint32, vp, vp, vp, vp, u32p]),
         'zkgpu_rccl_reductions': (u64, [vp]),
         'zkgpu_rccl_note': (sz, [vp, ctypes.c_char_p, sz]),
@@ -666,6 +667,23 @@ def generic_selftest(p, op, a, b=0):
     if rc:
         raise ZkGpuError('zkgpu_generic_selftest failed (%d)' % rc)
     return sum(int(out[i]) << (32 * i) for i in range(n))
+
+
+def mont_field_params(p):
+    """Test hook (include/zkgpu.h zkgpu_mont_field_params): the constants the Montgomery kernels are launched with for the
+    odd characteristic p, derived on the host; Python integers out."""
+    L = lib()
+    mod = int(p).to_bytes((int(p).bit_length() + 7) // 8 or 1, 'little')
+    P, R2, ONE = ((ctypes.c_uint32 * 16)() for _ in range(3))
+    out = (ctypes.c_uint32 * 7)()
+    rc = L.zkgpu_mont_field_params(mod, len(mod), P, R2, ONE, out)
+    if rc:
+        raise ZkGpuError('zkgpu_mont_field_params: not a modulus of the Montgomery path (%d)' % rc)
+
+    def val(w):
+        return sum(int(w[i]) << (32 * i) for i in range(16))
+    return {'p': val(P), 'r2': val(R2), 'one': val(ONE), 'nwords': int(out[0]), 'n0inv': int(out[1]),
+            'dot_rounds': [int(out[2 + k]) for k in range(4)], 'lazy_dot3': int(out[6])}
 
 
 def r1cs_generic_selftest(p, op, x, y=None, z=0):

@@ -1298,6 +1298,27 @@ int zkgpu_r1cs_generic_selftest(const uint8_t* modulus_le, size_t modulus_len, i
     return 2;
   }
 }
+// The constants the Montgomery kernels are launched with, derived on the host (Engine::mont_field_params): CPU-tier tests.
+int zkgpu_mont_field_params(const uint8_t* modulus_le, size_t modulus_len, uint32_t* p, uint32_t* r2, uint32_t* one,
+                            uint32_t out[7]) {
+  try {
+    FieldHost f;
+    f.init(Value(modulus_le, modulus_le + modulus_len), false);
+    if (f.is_two || f.generic) return 2;
+    // (the layout of zkgpu::FieldParams, device/args.hpp: three values of kMontWords words, then seven words)
+    uint32_t fp[Engine::kFieldParamsBytes / 4] = {0};
+    Engine::mont_field_params(f, fp);
+    memcpy(p, fp, 4 * kMontWords);
+    memcpy(r2, fp + kMontWords, 4 * kMontWords);
+    memcpy(one, fp + 2 * kMontWords, 4 * kMontWords);
+    out[0] = fp[3 * kMontWords + 1];                                  // nwords
+    out[1] = fp[3 * kMontWords];                                      // n0inv
+    for (int k = 0; k < 5; ++k) out[2 + k] = fp[3 * kMontWords + 2 + k];   // dot_rounds[4], lazy_dot3
+    return 0;
+  } catch (const std::exception&) {
+    return 2;
+  }
+}
 // wire-table slots of the values segment k hands to segment k + 1, in carry order (after zkgpu_finalize)
 int zkgpu_field_segment_carried(const zkgpu_session* s, uint32_t k, uint32_t* slots, uint32_t cap) {
   if (!s || !s->finalized || k >= s->prev.size() || cap < s->prev[k]->carried_out.size()) return 1;

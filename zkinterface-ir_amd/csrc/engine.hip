@@ -359,6 +359,38 @@ void Engine::upload_window(const void* entries, uint64_t n_entries, size_t entry
   window_entries_.push_back(n_entries);
 }
 
+// The constants the Montgomery kernels take by value (zkgpu::FieldParams), from the host's description of the field: host
+// arithmetic only.  load_program fills its kernarg copy with this; zkgpu_mont_field_params hands it to the CPU-tier tests.
+void Engine::mont_field_params(const FieldHost& f, void* out) {
+  zkgpu::FieldParams fp;
+  memset(&fp, 0, sizeof fp);
+  memcpy(fp.p, f.p, sizeof fp.p);
+  memcpy(fp.r2, f.r2, sizeof fp.r2);
+  memcpy(fp.one, f.one, sizeof fp.one);
+  fp.n0inv = f.n0inv;
+  fp.nwords = f.nwords;
+  // lazily reduced sums of K Montgomery products are below (K * p / R + 1) * p: ceil(K * p / R) conditional
+  // subtractions make them canonical.  In integers over the words of p: a quotient of floating-point numbers rounds
+  // 3 * p / R to exactly 2 for a p within 2^-64 of 2 / 3 * R and comes out one subtraction short.
+  if (!f.is_two && f.nwords >= 2) {
+    for (uint32_t k = 1; k <= 4; ++k) {
+      uint64_t c = 0;
+      bool low = false;                 // K * p mod R != 0
+      for (uint32_t i = 0; i < f.nwords; ++i) {
+        c += (uint64_t)k * f.p[i];
+        low |= (uint32_t)c != 0;
+        c >>= 32;
+      }
+      fp.dot_rounds[k - 1] = std::min<uint32_t>(std::max<uint32_t>((uint32_t)c + (low ? 1 : 0), 1), k);
+    }
+    // p / R from the top 64 bits of p, rounded up; the margin below 1 is far wider than the rounding of these products
+    const long double rho = ((long double)(((uint64_t)f.p[f.nwords - 1] << 32) | f.p[f.nwords - 2]) + 1.0L) / 18446744073709551616.0L;
+    const long double a3 = 3 * rho + 1;
+    fp.lazy_dot3 = (a3 * rho < 0.999L && a3 * a3 * rho < 0.999L) ? 1 : 0;
+  }
+  memcpy(out, &fp, sizeof fp);
+}
+
 void Engine::load_program(const Schedule& s, const FieldHost& f, uint32_t n_instance, uint32_t n_witness, uint32_t n_carry,
                           uint32_t carry_words) {
   use_device();
@@ -379,24 +411,7 @@ void Engine::load_program(const Schedule& s, const FieldHost& f, uint32_t n_inst
   if (!in_stride_set_) in_stride_ = elem_bytes_;
   if (in_stride_ < elem_bytes_ || (!boolean_ && in_stride_ % 4)) throw std::runtime_error("Engine: the input stride is narrower than the field's limbs");
   zkgpu::FieldParams fp;
-  memset(&fp, 0, sizeof fp);
-  memcpy(fp.p, f.p, sizeof fp.p);
-  memcpy(fp.r2, f.r2, sizeof fp.r2);
-  memcpy(fp.one, f.one, sizeof fp.one);
-  fp.n0inv = f.n0inv;
-  fp.nwords = f.nwords;
-  // lazily reduced sums of K Montgomery products are below (K * p / R + 1) * p: ceil(K * p / R) conditional
-  // subtractions make them canonical.  p / R from the top 64 bits of p, rounded up.
-  if (!f.is_two && f.nwords >= 2) {
-    const long double rho = ((long double)(((uint64_t)f.p[f.nwords - 1] << 32) | f.p[f.nwords - 2]) + 1.0L) / 18446744073709551616.0L;
-    for (int k = 1; k <= 4; ++k) {
-      uint32_t r = (uint32_t)(k * rho);
-      if ((long double)r < k * rho) ++r;
-      fp.dot_rounds[k - 1] = std::min<uint32_t>(std::max<uint32_t>(r, 1), (uint32_t)k);
-    }
-    const long double a3 = 3 * rho + 1;
-    fp.lazy_dot3 = (a3 * rho < 0.999L && a3 * a3 * rho < 0.999L) ? 1 : 0;
-  }
+  mont_field_params(f, &fp);
   memset(field_params_, 0, sizeof field_params_);
   memcpy(field_params_, &fp, sizeof fp);
   generic_ = f.generic;

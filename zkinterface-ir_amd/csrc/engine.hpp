@@ -39,6 +39,10 @@ class Engine {
   // n_carry values of carry_words 32-bit words each arrive from the previous field segment of the session (TK_CARRY)
   void load_program(const Schedule& s, const FieldHost& f, uint32_t n_instance, uint32_t n_witness, uint32_t n_carry = 0,
                     uint32_t carry_words = 0);
+  // zkgpu::FieldParams of a Montgomery field (p, r2, one, n0inv, nwords, dot_rounds[4], lazy_dot3: device/args.hpp) as
+  // load_program hands it to the kernels; `out` holds kFieldParamsBytes.  Host arithmetic only, no device call.
+  static constexpr size_t kFieldParamsBytes = 256;
+  static void mont_field_params(const FieldHost& f, void* out);
   // The arithmetic of the any-modulus kernels (device/generic_kernels.hpp) run on the HOST -- the same functions -- for
   // the CPU-tier tests: op 0 add, 1 mul, 2 reduce(a), 3 and, 4 xor over f.nwords words each.  Returns non-zero if `f`
   // is not a generic field or the op is unknown.
@@ -224,7 +228,7 @@ class Engine {
   // pinned wires (Evaluator::get) need the LDS-resident values written back to HBM
   void set_writeback(bool on) { force_writeback_ = on; graph_dirty_ = true; }
  private:
-  unsigned char field_params_[256];  // zkgpu::FieldParams, opaque here
+  unsigned char field_params_[kFieldParamsBytes];  // zkgpu::FieldParams, opaque here
 };
 
 // One process driving several GPUs: the {satisfied, failed} counters of engines on DISTINCT devices are combined by an
