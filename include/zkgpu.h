@@ -122,9 +122,16 @@ uint32_t zkgpu_n_witness(const zkgpu_session* s);
 /* schedule facts: out[0]=levels out[1]=launches out[2]=slots out[3]=widest level out[4]=sequential launches */
 /* ... out[5]=device ops out[6]=constant words out[7]=words per constant */
 int zkgpu_schedule_info(const zkgpu_session* s, uint64_t out[8]);
+/* what the scheduler's rewrites did: out[0]=stores left out (values whose entry carries bit 14 / 15, below)
+ * out[1]=gates evaluated inside a reader (pairs included) out[2]=shared producers of pair entries
+ * out[3]=copies not materialised out[4]=exponent ladders replaced by one entry; out[5..7] = 0 */
+int zkgpu_schedule_counters(const zkgpu_session* s, uint64_t out[8]);
 /* the device program itself (host-logic tests interpret it without a GPU): ops4 points at 8 words per op
- * {dst, kind | a_expr << 8 | b_expr << 10 | second << 12, a0, a1, b0, b1, dst2, c0} (expr: 0 = the slot,
- * 1 = add(x0,x1), 2 = mul(x0,x1); second != 0: pair entry, also dst2 = add (1) / mul (2) of operand a and slot c0),
+ * {dst, kind | a_expr << 8 | b_expr << 10 | second << 12 | no_store << 14, a0, a1, b0, b1, dst2, c0} (expr: 0 = the
+ * slot, 1 = add(x0,x1), 2 = mul(x0,x1); second != 0: pair entry, also dst2 = add (1) / mul (2) of operand a and slot c0;
+ * no_store bit 14: the value of dst, bit 15: the value of dst2 is computed but not written to the wire table -- it is
+ * closed (dropped by its owner, or the relation has ended and it is not alive) and has no reader, so nothing could load
+ * it; dst / dst2 are the slots they would have been.  Option "dead_stores"; the fused program only),
  * launches4 = {first,count,ops_per_wave,sequential} per launch, const_words = constant pool in device form,
  * slot_of[i] = wire-table slot of tape op i (0xFFFFFFFF for asserts).  An operand of and / xor over a field other than
  * GF(2) may be 0x80000000 | (2 + 4 * position + stream) instead of a slot: the raw value of that input (stream 0 instance,
@@ -242,6 +249,8 @@ size_t zkgpu_input_modes(const zkgpu_session* s, int witness, uint8_t* out, size
  * passes the primality test; never with retain_all; default 1),
  * "pair" = 0|1 (an Add/Mul read by exactly two Add/Mul gates of one level is evaluated once inside a pair entry
  * that produces both readers' values; part of "fuse", never with retain_all),
+ * "dead_stores" = 0|1 (a value with no reader that nobody can ask for any more is computed but not stored: bits 14 / 15
+ * of its entry, zkgpu_schedule_dump; part of "fuse", never with retain_all; default 1),
  * "propagate_copies" = 0|1 (readers use a copy's source, unobserved copies are not materialised; never with retain_all),
  * "bool_path" = "auto" | "hbm" | "lds"  (GF(2): HBM wire table, or the whole wire table of a
  * 32-witness slice resident in one CU's LDS when the live wires fit in 160 KiB).  Set before zkgpu_set_inputs*.

@@ -81,6 +81,7 @@ def lib():
         'zkgpu_n_instance': (u32, [vp]),
         'zkgpu_n_witness': (u32, [vp]),
         'zkgpu_schedule_info': (ci, [vp, u64p]),
+        'zkgpu_schedule_counters': (ci, [vp, u64p]),
         'zkgpu_schedule_dump': (ci, [vp, vp, vp, vp, vp]),
         'zkgpu_lds_program': (ci, [vp, u32, u64p, vp, vp, vp, vp]),
         'zkgpu_set_inputs': (ci, [vp, vp, vp, u32]),
@@ -375,6 +376,12 @@ class Evaluator:
         keys = ['levels', 'launches', 'slots', 'max_width', 'sequential_launches', 'device_ops', 'const_words',
                 'words_per_const']
         return dict(zip(keys, list(out)))
+
+    def schedule_counters(self):
+        """what the scheduler's rewrites did (include/zkgpu.h zkgpu_schedule_counters)"""
+        out = (ctypes.c_uint64 * 8)()
+        self._ck(self.L.zkgpu_schedule_counters(self.h, out))
+        return dict(zip(['stores_elided', 'absorbed', 'paired', 'copies_elided', 'ladders'], list(out)))
 
     def strand_levels(self, launch):
         """(level bounds relative to the launch's first entry, LDS-resident values) of a strand, None for any other launch

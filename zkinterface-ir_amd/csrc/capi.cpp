@@ -109,6 +109,7 @@ struct zkgpu_session {
   bool fuse = true;
   bool propagate_copies = true;
   bool pair = true;
+  bool dead_stores = true;
   bool fermat = true;
   uint32_t n_streams = 2;
   bool xcd_map = true;
@@ -216,6 +217,7 @@ ScheduleOptions schedule_options(const zkgpu_session* s, bool retain_all) {
   opt.retain_all = retain_all;
   opt.sort_by_operand = s->sort_by_operand;
   opt.pair = s->pair;
+  opt.dead_stores = s->dead_stores;
   opt.fermat = s->fermat;
   opt.fuse = s->fuse;
   opt.propagate_copies = s->propagate_copies;
@@ -1447,6 +1449,18 @@ int zkgpu_schedule_info(const zkgpu_session* s, uint64_t out[8]) {
   return 0;
 }
 
+int zkgpu_schedule_counters(const zkgpu_session* s, uint64_t out[8]) {
+  if (!s || !s->finalized) return 1;
+  const Schedule& sc = seg_sched(s, inspected(s));
+  memset(out, 0, 8 * sizeof(uint64_t));
+  out[0] = sc.n_stores_elided;
+  out[1] = sc.n_absorbed;
+  out[2] = sc.n_paired;
+  out[3] = sc.n_copies_elided;
+  out[4] = sc.n_ladders;
+  return 0;
+}
+
 int zkgpu_lds_program(zkgpu_session* s, uint32_t block_rows, uint64_t sizes[6], uint16_t* ops8, uint16_t* rows,
                       uint32_t* blocks, uint32_t* chunks) {
   return guarded(s, [&] {
@@ -1642,7 +1656,7 @@ int zkgpu_set_option(zkgpu_session* s, const char* key, const char* value) {
     const std::string k = key ? key : "", v = value ? value : "";
     // the scheduler of a streamed ingest took its options when the first window was cut: a later change would be ignored
     // silently by the windows already scheduled -- refuse it instead
-    if (s->stream && (k == "fuse" || k == "pair" || k == "fermat" || k == "propagate_copies" || k == "sort_by_operand" ||
+    if (s->stream && (k == "fuse" || k == "pair" || k == "dead_stores" || k == "fermat" || k == "propagate_copies" || k == "sort_by_operand" ||
                       k == "bank_aware" || k == "strand_width" || k == "strand_lds" || k == "strand_prefetch" || k == "strand_merge" || k == "strand_reassociate" || k == "strand_split_inputs" || k == "bool_narrow_width" || k == "schedule_threads"))
       throw std::runtime_error(k + ": the streamed schedule has started (option \"stream\"); set scheduling options before the first Relation message");
     if (k == "bool_path") {
@@ -1720,6 +1734,8 @@ int zkgpu_set_option(zkgpu_session* s, const char* key, const char* value) {
       s->fermat = v != "0";
     } else if (k == "pair") {
       s->pair = v != "0";
+    } else if (k == "dead_stores") {
+      s->dead_stores = v != "0";
     } else if (k == "propagate_copies") {
       s->propagate_copies = v != "0";
     } else if (k == "fuse") {

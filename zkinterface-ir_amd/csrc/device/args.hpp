@@ -71,7 +71,8 @@ struct TapeOp {
   u32 kind;
 };
 
-// 32-byte program entry of the fused schedule (host: DevOp2, schedule.hpp)
+// 32-byte program entry of the fused schedule (host: DevOp2, schedule.hpp).  kind: bits 0-7 OpKind, 8-9 / 10-11 operand
+// expressions, 12-13 pair entry (dst2 = pad0, its own operand pad1), 14 / 15 kNoStoreDst / kNoStoreDst2
 struct TapeOp2 {
   u32 dst, kind, a0, a1, b0, b1, pad0, pad1;
 };
@@ -83,6 +84,11 @@ constexpr u32 kOperandIsSource = 0x80000000u;
 constexpr u32 kLaneFlagNonCanonical = 1u;
 // a slot number of a STRAND's entry with this bit names value k of the workgroup's LDS, [k][chunk][lane] (host: schedule.hpp)
 constexpr u32 kSlotInLds = 0x40000000u;
+// Bits 14 / 15 of a fused entry's kind word: the value the entry computes for `dst` / for `dst2` (pad0, the second gate of
+// a pair entry) is NOT written to the wire table.  The scheduler sets them on values that are closed and have no reader
+// (schedule.cpp fuse_and_pair): the arithmetic runs as for any other entry, only the store nobody could load is left out.
+// Wave-uniform like the rest of the entry: the kernels branch around the store on the scalar path.
+constexpr u32 kNoStoreDst = 1u << 14, kNoStoreDst2 = 1u << 15;
 
 // What only the input arms of the replay kernels read (instance / witness / carried values and their modes): kept behind
 // ONE pointer so that the eleven words do not sit in SGPRs through every other arm of the cold kernels (with them in the

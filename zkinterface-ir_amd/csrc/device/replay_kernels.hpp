@@ -429,6 +429,22 @@ __device__ __forceinline__ void load_entry_pair_words(const TapeOp2* ops, u32 i,
 //   kFusedMisc -- every kind except the integer bit operations over an odd field (inputs, constants, copies,
 //                 AddConstant/MulConstant, AssertZero, the `x != 0` indicator, and Add/Mul for sequential segments).
 //   kFusedAll  -- kFusedMisc + and / xor over an odd field (two from_mont + one to_mont each, evaluator.rs:924-933).
+// The result of an entry whose store is left out (kNoStoreDst / kNoStoreDst2) has no use the compiler can see, and the
+// Montgomery routines are plain (non-volatile) asm: left alone hipcc sinks them into the store's branch or deletes them.
+// The reference runs every gate and the gate rate counts every gate: on the path without the store an empty volatile asm
+// takes the words as VGPR inputs, so both sides of the (scalar, wave-uniform) branch use the result and it is computed
+// in front of it.
+template <int N>
+__device__ __forceinline__ void keep_computed(const Fp<N>& r) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) asm volatile("" ::"v"(r.w[i]));
+}
+template <int N, bool LDS>
+__device__ __forceinline__ void slot_store_unless(bool no_store, uint4* __restrict__ T, u32 slot, u32 lane, const Fp<N>& r) {
+  if (no_store) keep_computed<N>(r);
+  else slot_store<N, LDS>(T, slot, lane, r);
+}
+
 template <int N, bool LDS = false>
 __device__ __forceinline__ void fused_addmul(const TapeOp2& op, uint4* __restrict__ T, const FieldParams& fp, u32 lane = 0) {
   const u32 kind = op.kind & 0xFF, ea = (op.kind >> 8) & 3, eb = (op.kind >> 10) & 3;
@@ -440,8 +456,10 @@ __device__ __forceinline__ void fused_addmul(const TapeOp2& op, uint4* __restric
   y0 = slot_load<N, LDS>(T, op.b0, lane);
   if (eb) y1 = slot_load<N, LDS>(T, op.b1, lane);
   u32 pv[N];   // the words of p in VGPRs, once per entry: every carry chain below subtracts them (fp_mont.hpp)
-  if constexpr (N <= 12) p_words_resident<N>(pv, fp);
-  else p_words<N>(pv, fp);   // (beyond 384 bits the kernel is short of registers: let hipcc rematerialise them)
+  // (from 384 bits on the kernel is short of registers: let hipcc rematerialise them.  At 12 words the resident copy
+  // and the branches around the stores together leave the copy in scratch memory; rematerialised it takes 67 VGPRs)
+  if constexpr (N <= 10) p_words_resident<N>(pv, fp);
+  else p_words<N>(pv, fp);
   if (ea) x0 = ea == 1 ? fp_add<N>(x0, x1, fp, pv) : fp_mul<N>(x0, x1, fp, pv);
   if (eb) y0 = eb == 1 ? fp_add<N>(y0, y1, fp, pv) : fp_mul<N>(y0, y1, fp, pv);
   Fp<N> r = kind == OP_ADD ? fp_add<N>(x0, y0, fp, pv) : fp_mul<N>(x0, y0, fp, pv);
@@ -450,12 +468,13 @@ __device__ __forceinline__ void fused_addmul(const TapeOp2& op, uint4* __restric
   if (pair) {
     // a second gate of the same level fed by the shared producer X: store the first result, fetch the second
     // gate's other operand into registers the first no longer needs, and let the common store write it
-    slot_store<N, LDS>(T, dst_slot, lane, r);
+    slot_store_unless<N, LDS>((op.kind & kNoStoreDst) != 0, T, dst_slot, lane, r);
     y0 = slot_load<N, LDS>(T, op.pad1, lane);
     r = pair == 1 ? fp_add<N>(x0, y0, fp, pv) : fp_mul<N>(x0, y0, fp, pv);
     dst_slot = op.pad0;
   }
-  slot_store<N, LDS>(T, dst_slot, lane, r);
+  // (the kind word is wave-uniform, in an SGPR: a scalar test and a branch around the store)
+  slot_store_unless<N, LDS>((op.kind & (pair ? kNoStoreDst2 : kNoStoreDst)) != 0, T, dst_slot, lane, r);
 }
 
 // The chain of a strand: an Add/Mul entry (not a pair) whose operands and result all live in LDS.  fused_addmul reaches
@@ -552,7 +571,7 @@ __device__ __forceinline__ void fused_entry(const TapeOp2& op, uint4* __restrict
     }
     default: has_out = false; break;
   }
-  if (has_out) slot_store<N, LDS>(T, op.dst, lane, r);
+  if (has_out) slot_store_unless<N, LDS>((op.kind & kNoStoreDst) != 0, T, op.dst, lane, r);
 }
 
 template <int N, int CLS>

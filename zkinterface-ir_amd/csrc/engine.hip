@@ -304,7 +304,15 @@ void Engine::validate_program(const Schedule& s, uint32_t n_instance, uint32_t n
         if (s.fused) {
           const DevOp2& d = s.ops2[i];
           const uint32_t kind = d.kind & 0xFF, ea = (d.kind >> 8) & 3, eb = (d.kind >> 10) & 3, second = (d.kind >> 12) & 3;
-          if ((d.kind >> 14) != 0 || ((ea || eb || second) && kind != TK_ADD && kind != TK_MUL)) fail(i, "its kind word");
+          if ((d.kind >> 16) != 0 || ((ea || eb || second) && kind != TK_ADD && kind != TK_MUL)) fail(i, "its kind word");
+          // a store left out (kNoStoreDst / kNoStoreDst2): of a kind that stores a plain wire-table value, the second one of
+          // a pair entry only; dst / dst2 are checked as the slots they are either way
+          if (d.kind & zkgpu::kNoStoreDst) {
+            const bool ok = kind == TK_ADD || kind == TK_MUL || kind == TK_ADDC || kind == TK_MULC || kind == TK_COPY || kind == TK_NZ ||
+                            kind == TK_NOT || kind == TK_CONST || kind == TK_INSTANCE || kind == TK_WITNESS || kind == TK_CARRY;
+            if (!ok || (d.dst & zkgpu::kSlotInLds)) fail(i, "the no-store bit of its kind word");
+          }
+          if ((d.kind & zkgpu::kNoStoreDst2) && (!second || (d.pad0 & zkgpu::kSlotInLds))) fail(i, "the second no-store bit of its kind word");
           check(i, kind, d.dst, d.a0, d.a1, d.b0, d.b1, ea, eb, second, d.pad0, d.pad1, d.a1);
         } else {
           const DevOp& d = s.ops[i];

@@ -247,6 +247,7 @@ struct StreamScheduler::Impl {
   std::vector<uint8_t> kind, state;
   std::vector<uint32_t> ra, rb;          // operands resolved through copy chains (handles)
   std::vector<uint32_t> pair_second;     // first gate of a pair entry -> second gate
+  std::vector<uint8_t> unread;           // value that is closed and has no reader: its store is left out (fuse_and_pair; empty = none)
   std::vector<uint32_t> order;           // live entries in program order
   std::vector<uint64_t> level_start;
   uint32_t n_wlevels = 0;
@@ -580,6 +581,7 @@ void StreamScheduler::Impl::fuse_and_pair() {
   const std::vector<uint32_t>& level = s.level_of;
   const uint32_t n = hi - lo;
   pair_second.clear();
+  unread.clear();
   if (!s.fused) return;   // (opt.fuse, no retain_all, a Montgomery field)
   std::vector<uint32_t> reads(n, 0), reader(n, 0), reader0(n, 0);
   std::vector<uint8_t> has_absorbed(n, 0);
@@ -631,6 +633,25 @@ void StreamScheduler::Impl::fuse_and_pair() {
       extend(ra[i - lo], level[c1]);
       extend(rb[i - lo], level[c1]);
     }
+  }
+  // ---- stores nobody can observe ---------------------------------------------
+  // A closed value has all its readers in this window; with none of them (counted above on ra / rb, i.e. behind copy
+  // propagation and the ladder rewrite -- an absorbed producer or a pair's shared one has its readers by construction)
+  // no kernel, no Evaluator::get and no later window can ever load what its entry stores.  The entry stays where it is,
+  // keeps its slot and does its arithmetic (the reference runs every gate, and so do we); emit_entries() marks it
+  // kNoStoreDst / kNoStoreDst2 and the kernels branch around the store.  The rule looks at nothing but the tape, the
+  // window and the options: two ingests cut at the same places give the same bits.
+  if (opt.dead_stores) {
+    auto storable = [](uint8_t k) {
+      switch (k) {
+        case TK_ADD: case TK_MUL: case TK_ADDC: case TK_MULC: case TK_COPY: case TK_NZ: case TK_NOT: case TK_CONST:
+        case TK_INSTANCE: case TK_WITNESS: case TK_CARRY: return true;
+        default: return false;   // (and / xor over an odd field keep their store: rare, and their operands are not plain slots)
+      }
+    };
+    unread.assign(n, 0);
+    for (uint32_t i = lo; i < hi; ++i)
+      unread[i - lo] = (st(i) == ST_ENTRY || st(i) == ST_PAIR_SECOND) && storable(kind[i - lo]) && reads[i - lo] == 0 && closed(i);
   }
 }
 
@@ -1411,7 +1432,11 @@ void StreamScheduler::Impl::emit_entries() {
   if (s.fused) {
     const size_t at = s.ops2.size();
     s.ops2.resize(at + n_live);
+    std::atomic<uint64_t> n_elided{0};
+    // (a value in a strand's LDS is not a wire-table store: left alone)
+    auto no_store = [&](uint32_t h) { return !unread.empty() && unread[h - lo] && !(s.slot_of[h] & kSlotInLds); };
     parallel_slices(n_live, 1 << 16, [&](size_t k_lo, size_t k_hi) {
+    uint64_t elided = 0;
     for (size_t k = k_lo; k < k_hi; ++k) {
       const uint32_t i = order[k];
       const uint8_t kd = kind[i - lo];
@@ -1440,6 +1465,7 @@ void StreamScheduler::Impl::emit_entries() {
             d.kind |= (kind[j - lo] == TK_ADD ? 1u : 2u) << 12;
             d.pad0 = s.slot_of[j];
             d.pad1 = s.slot_of[ra[j - lo] == sh ? rb[j - lo] : ra[j - lo]];
+            if (no_store(j)) { d.kind |= kNoStoreDst2; ++elided; }
           } else {
             operand(x, &d.a0, &d.a1, 8);
             operand(y, &d.b0, &d.b1, 10);
@@ -1464,9 +1490,12 @@ void StreamScheduler::Impl::emit_entries() {
           break;
         default: break;
       }
+      if (kd != TK_ASSERT && no_store(i)) { d.kind |= kNoStoreDst; ++elided; }
       s.ops2[at + k] = d;
     }
+    n_elided += elided;
     });
+    s.n_stores_elided += n_elided;
     return;
   }
   const size_t at = s.ops.size();
@@ -1667,6 +1696,7 @@ void StreamScheduler::Impl::prefetch_strand_inputs(size_t first_launch) {
           if (m == kInf) continue;
           const uint32_t stream = kind == TK_WITNESS ? 1u : 0u, position = e.a0;
           add[t].push_back(DevOp2{m, TK_INPUT_RAW, position, stream, 0, 0, 0, 0});
+          if (e.kind & kNoStoreDst) --s.n_stores_elided;   // (the two halves of an input always store: an unread input of a chain is not worth an arm of the kernel)
           e.kind = TK_INPUT_CONV;
           e.a0 = m;
           e.a1 = stream;
@@ -1698,7 +1728,7 @@ void StreamScheduler::Impl::prefetch_strand_inputs(size_t first_launch) {
           const uint32_t m = lds_value(t, q);
           if (m == kInf) continue;
           add[t].push_back(DevOp2{m, TK_MUL, x, 0, y, 0, 0, 0});
-          e.kind = TK_MUL;
+          e.kind = TK_MUL | (e.kind & kNoStoreDst);
           e.a0 = z;
           e.a1 = 0;
           e.b0 = m;

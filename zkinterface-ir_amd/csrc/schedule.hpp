@@ -25,6 +25,9 @@ namespace zki {
 // table (device/args.hpp kSlotInLds).  Only entries of a strand's launch may carry such slots.
 constexpr uint32_t kSlotInLds = 0x40000000u;
 constexpr uint32_t kStrandLdsBytes = 128 * 1024;   // of the CU's 160 KiB
+// Bits of a fused entry's kind word (device/args.hpp): the value `dst` / `dst2` names is computed but not written to the
+// wire table -- it is closed and has no reader, so nothing can observe the store (ScheduleOptions::dead_stores)
+constexpr uint32_t kNoStoreDst = 1u << 14, kNoStoreDst2 = 1u << 15;
 
 struct DevOp {  // == zkgpu::TapeOp (device/replay_kernels.hpp)
   uint32_t dst, a, b, kind;
@@ -33,7 +36,7 @@ struct DevOp {  // == zkgpu::TapeOp (device/replay_kernels.hpp)
 // Program entry when gate fusion is on: an Add/Mul operand may itself be an Add/Mul of two slots that is
 // evaluated in registers (the absorbed producer is never written to the wire table).
 //   kind: bits 0-7 main op (TapeKind), bits 8-9 / 10-11: operand a / b is 0 = slot a0 / b0,
-//         1 = add(a0,a1), 2 = mul(a0,a1)
+//         1 = add(a0,a1), 2 = mul(a0,a1); bits 12-13: pair entry; bit 14 / 15: kNoStoreDst / kNoStoreDst2
 struct DevOp2 {  // == zkgpu::TapeOp2 (device/replay_kernels.hpp)
   uint32_t dst, kind, a0, a1, b0, b1, pad0, pad1;
 };
@@ -65,6 +68,7 @@ struct ScheduleOptions {
   bool fuse = true;                 // absorb single-reader Add/Mul producers into their consumer (never with retain_all)
   bool fermat = true;               // a Switch exponent ladder x^(p-1), p prime, becomes one `x != 0` entry (never with retain_all)
   bool pair = true;                 // one entry for the two same-level readers of a producer nobody else reads (never with retain_all)
+  bool dead_stores = true;          // a closed value without a reader is computed but not stored (fused format only: never with retain_all)
   bool propagate_copies = true;     // readers use a copy's source; unobserved copies are not materialised (never with retain_all)
   std::vector<uint32_t> pinned;     // handles that must stay readable after the replay (Evaluator::get)
   bool pinned_are_carried = false;  // ... because the next field segment takes them over from the wire table (capi.cpp)
@@ -85,6 +89,7 @@ struct Schedule {
   uint64_t n_copies_elided = 0;
   uint64_t n_ladders = 0;           // exponent ladders replaced by one entry each
   uint64_t n_paired = 0;            // producers evaluated inside a pair entry (counted in n_absorbed too)
+  uint64_t n_stores_elided = 0;     // values whose entry carries kNoStoreDst / kNoStoreDst2
   uint64_t n_strand_inputs_split = 0;    // inputs of a strand fetched ahead of their conversion
   uint64_t n_strand_reassociated = 0;    // products of a strand computed off its dependency chain
   uint64_t n_strand_levels_joined = 0;   // strand levels that run behind the level in front of them without a barrier
@@ -127,6 +132,7 @@ struct Schedule {
     c.n_copies_elided = n_copies_elided;
     c.n_ladders = n_ladders;
     c.n_paired = n_paired;
+    c.n_stores_elided = n_stores_elided;
     c.n_strand_prefetches = n_strand_prefetches;
     c.n_strand_levels_joined = n_strand_levels_joined;
     c.n_strand_reassociated = n_strand_reassociated;
